@@ -1,7 +1,15 @@
 """Throughput benchmark of the CLIP ViT-L/14-336 embedding path, one process per GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload clip|pacl|negclip|sparc] [--batch B]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line (`roofline`,
+`cpu_baseline` null, no `every_row`).  `--full` adds the legs described below that take runs of their
+own: the per-kernel profile pass and the dominant kernel's roofline, the `every_row` leg and the CPU
+baseline.  `--dump-outputs DIR` writes what the last timed step returned (rank 0) as DIR/<name>.npy
+(float32; at most 64 MB in all, a fixed seeded sample of anything larger); the inputs are seeded, so
+two builds can be compared output for output.
 
 `--gpus N > 1` without a launcher re-launches this script under torch.distributed.run as a child
 process (before any GPU call) and exits with its status; it never silently runs one rank.
@@ -27,7 +35,7 @@ Workloads (BASELINE.json configs; a "step" is one pass of the hot path over one 
            train_sparc.py:93,105 computes it after nn.DataParallel's gather) for B = 256 per GPU.
 
 Prints ONE JSON line (rank 0).  value = image-text pairs/s over all ranks (weak scaling: B pairs
-per GPU per step), inputs resident in HBM before the timed region.  `roofline` reports the
+per GPU per step), inputs resident in HBM before the timed region.  With --full: `roofline` reports the
 dominant kernel (by total time in an untimed profile pass), measured with HIP events on its stream
 over the timed steps (only its launches carry events there); for pacl it also carries the pooling
 kernel's HBM rate.  `cpu_baseline` times the reference's CPU forward (oracle/clip_torch_cpu.py: the
@@ -153,6 +161,38 @@ def load_mfma_busy(tag):
     return None
 
 
+# ----------------------------------------------------------------------------------- output dump
+DUMP_BYTES = 64 << 20
+
+
+def named_outputs(ret, names):
+    """name -> tensor of what a step returned: one tensor or a tuple of them, named by the builder."""
+    if not isinstance(ret, (tuple, list)):
+        ret = (ret,)
+    assert len(ret) == len(names), (len(ret), names)
+    return dict(zip(names, ret))
+
+
+def dump_outputs(path, named):
+    """Write each output as path/<name>.npy (float32; float64 stays float64), DUMP_BYTES in all: an
+    array over its equal share is cut to a sorted sample of its flattened elements (seed 0, so the
+    same elements in every run and every build)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(named))
+    for name, t in named.items():
+        if isinstance(t, torch.Tensor):
+            t = t.detach()
+            t = (t if t.dtype == torch.float64 else t.float()).cpu().numpy()
+        a = np.asarray(t)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        log(f"  dumped {name} {a.dtype} {list(a.shape)} -> {os.path.join(path, name + '.npy')}")
+
+
 # ----------------------------------------------------------------------------------- workloads
 def pooled_prune_flops(cfg, on=True, eot=None):
     """FLOPs per pair NOT executed by pooled-only calls (ce_set_pooled_prune): the image tower's last
@@ -224,7 +264,8 @@ def build_clip(args, dev, rank, world):
                 fi.record_stream(main)
             main.wait_stream(side)
             ft.record_stream(main)
-        return exch.get_logits(fi, ft, scale)
+        li, lt = exch.get_logits(fi, ft, scale)
+        return fi, ft, li, lt
 
     cfgd = {"workload": "CLIP ViT-L/14-336 encode_image + encode_text + normalise + contrastive logits "
                         "(BASELINE configs[1]: batch 256/GPU bf16)",
@@ -240,6 +281,7 @@ def build_clip(args, dev, rank, world):
                 # profiles/pmc_traffic.json was measured on this default configuration
                 pmc_tags=("gemm_fc_v", "gemm_qkv_v", "attn_v")
                 if B == 256 and not args.no_pooled_prune else (),
+                outputs=("image_features", "text_features", "logits_per_image", "logits_per_text"),
                 metric="image-text pairs/sec ViT-L/14-336", config=cfgd)
 
 
@@ -283,7 +325,7 @@ def build_pacl(args, dev, rank, world):
 
     def step():
         oi, ot = mod(imgs, caps)
-        return loss(oi, ot)
+        return oi, ot, loss(oi, ot)
 
     cfgd = {"workload": f"PACL patch-token forward ({cls.__name__}) + patch alignment/pooling + PACL ClipLoss "
                         "(BASELINE configs[2]: batch 512/GPU bf16)",
@@ -297,6 +339,7 @@ def build_pacl(args, dev, rank, world):
                 flops_exec_per_pair=FLOPS_PER_PAIR + PACL_HEAD_FLOPS + pool_flops - pt,
                 # profiles/pmc_traffic.json's pacl_pool entry was measured on this default configuration
                 pmc_tags=("pacl_pool",) if B == 512 and args.pacl_mode == "ones" else (),
+                outputs=("image_features", "text_features", "loss"),
                 metric="PACL image-text pairs/sec ViT-L/14-336", config=cfgd, hbm_kernel="pacl_pool")
 
 
@@ -422,9 +465,14 @@ def main():
                     help="pacl: time the train_pacl.py head training step instead of the forward")
     ap.add_argument("--sparc-forward", action="store_true",
                     help="sparc: time the forward + loss value only (default: the full training step)")
-    ap.add_argument("--cpu-batch", type=int, default=8, help="pairs per CPU-baseline run")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-timing", action="store_true", help="do not bracket kernels with HIP events")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: per-kernel profile pass + roofline, "
+                         "every_row, CPU baseline (each has its own --no-... switch)")
+    ap.add_argument("--cpu-batch", type=int, default=8, help="--full: pairs per CPU-baseline run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-timing", action="store_true", help="--full: do not bracket kernels with HIP events")
     ap.add_argument("--serial-towers", action="store_true", help="clip: both towers on one stream")
     ap.add_argument("--tower-priority", action="store_true", help="clip: image tower on a high-priority stream")
     ap.add_argument("--text-priority", action="store_true", help="clip: text tower on a high-priority stream")
@@ -433,7 +481,7 @@ def main():
     ap.add_argument("--no-pooled-prune", action="store_true",
                     help="run every tower's last block for all rows (A/B of ce_set_pooled_prune)")
     ap.add_argument("--no-every-row", action="store_true",
-                    help="skip the second timed leg with the pooled prune off (`every_row` in the JSON line)")
+                    help="--full: skip the second timed leg with the pooled prune off (`every_row` in the JSON line)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="N > 1: torch.distributed backend (nccl = RCCL over xGMI; gloo only to rehearse the "
                          "multi-rank code path with every rank on one device, --share-device)")
@@ -443,6 +491,8 @@ def main():
     ap.add_argument("--gemm-stagger", type=int, default=-1,
                     help="first-round stagger of the persistent residual GEMMs (x s_sleep 127, odd slots; A/B)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(relaunch(args.gpus))
@@ -487,7 +537,7 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    timing = not args.no_timing
+    timing = args.full and not args.no_timing
     profile = []
     if timing:
         # untimed profile pass: every kernel bracketed by HIP events -> per-kernel table (stderr) and
@@ -504,8 +554,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t_start = time.perf_counter()
+    ret = None
     for _ in range(args.steps):
-        step()
+        ret = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -513,6 +564,9 @@ def main():
     stats = engine.kernel_stats() if timing else []
     if timing:
         engine.set_timing(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, named_outputs(ret, W.get("outputs", ("loss",))))
+    del ret
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -521,7 +575,7 @@ def main():
     # the same K steps with every row of the last blocks computed (pooled prune off):
     # reported beside `value` so the step is also measured without the dead-row skipping
     every_row = None
-    if W.get("prunable", True) and not args.no_pooled_prune and not args.no_every_row:
+    if args.full and W.get("prunable", True) and not args.no_pooled_prune and not args.no_every_row:
         prev = engine.set_pooled_prune(False)
         step()
         if world > 1:
@@ -596,7 +650,7 @@ def main():
                                       "traffic": load_traffic(hk) if hk in W.get("pmc_tags", ()) else None}
 
     cpu = None
-    if world == 1 and not args.no_cpu_baseline and args.workload == "clip":
+    if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "clip":
         cpu = cpu_baseline(W["sd"], W["cfg"], args.cpu_batch)
         cpu["vs_gpu"] = round(value / cpu["value"], 1)
 
@@ -610,6 +664,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": round(1000 * elapsed / args.steps, 3),
         "higher_is_better": True,
         "scaling": "weak",

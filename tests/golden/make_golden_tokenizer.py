@@ -7,6 +7,7 @@ inputs (the texts) and outputs (ids, decoded strings) to tests/golden/tokenizer.
 source or data file is copied.
 
     python tests/golden/make_golden_tokenizer.py
+    python tests/golden/make_golden_tokenizer.py --synthetic    # with tests/golden/bpe_synthetic.txt.gz
 """
 import importlib.util
 import os
@@ -49,21 +50,26 @@ def load_reference():
 
 def main():
     mod = load_reference()
+    # --synthetic: the same record with tests/golden/bpe_synthetic.txt.gz (make_bpe_synthetic.py) as the
+    # merges file instead of the reference's own -> tokenizer_synthetic.npz
+    synthetic = "--synthetic" in sys.argv[1:]
+    bpe = {"bpe_path": os.path.join(HERE, "bpe_synthetic.txt.gz")} if synthetic else {}
+    name = "tokenizer_synthetic.npz" if synthetic else "tokenizer.npz"
     out = {"texts": np.array(TEXTS)}
     for clean in ("lower", "whitespace", "canonicalize"):
-        tok = mod.SimpleTokenizer(clean=clean)
+        tok = mod.SimpleTokenizer(clean=clean, **bpe)
         out[f"ids_{clean}"] = tok(TEXTS).numpy().astype(np.int64)
-    tok = mod.SimpleTokenizer()
+    tok = mod.SimpleTokenizer(**bpe)
     out["ids_ctx16"] = tok(TEXTS, context_length=16).numpy().astype(np.int64)
     enc = [tok.encode(t) for t in TEXTS]
     out["enc_len"] = np.array([len(e) for e in enc], dtype=np.int64)
     out["enc_flat"] = np.array([i for e in enc for i in e], dtype=np.int64)
     out["decoded"] = np.array([tok.decode(e) for e in enc])
-    extra = mod.SimpleTokenizer(additional_special_tokens=["<extra_a>", "<extra_b>"])
+    extra = mod.SimpleTokenizer(additional_special_tokens=["<extra_a>", "<extra_b>"], **bpe)
     out["ids_extra"] = extra(["x <extra_a> y <extra_b>", "plain"]).numpy().astype(np.int64)
     out["vocab_size"] = np.array([tok.vocab_size, extra.vocab_size], dtype=np.int64)
-    np.savez_compressed(os.path.join(HERE, "tokenizer.npz"), **out)
-    print("wrote tokenizer.npz", {k: v.shape for k, v in out.items()})
+    np.savez_compressed(os.path.join(HERE, name), **out)
+    print("wrote", name, {k: v.shape for k, v in out.items()})
 
 
 if __name__ == "__main__":

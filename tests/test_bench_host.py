@@ -34,5 +34,35 @@ def test_bench_cli_contract():
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--help"], capture_output=True, text=True,
                        timeout=300)
     assert r.returncode == 0, r.stderr
-    for flag in ("--gpus", "--steps", "--warmup", "--workload", "--no-pooled-prune", "--no-every-row"):
+    for flag in ("--gpus", "--steps", "--warmup", "--workload", "--no-pooled-prune", "--no-every-row", "--full",
+                 "--dump-outputs"):
         assert flag in r.stdout
+
+
+def test_named_outputs():
+    a, b = np.zeros(2), np.ones(3)
+    assert bench.named_outputs(a, ("loss",)) == {"loss": a}
+    d = bench.named_outputs((a, b), ("x", "y"))
+    assert list(d) == ["x", "y"] and d["x"] is a and d["y"] is b
+
+
+def test_dump_outputs_dtypes_and_cap(tmp_path, monkeypatch):
+    """float32 files (float64 kept), bf16 / integer tensors converted; an array over its share of the
+    byte cap is cut to the same seeded sample of its elements in every call."""
+    import torch
+    x = torch.arange(12, dtype=torch.float32).reshape(3, 4)
+    named = {"bf": x.to(torch.bfloat16), "f64": x.double(), "i": torch.tensor(5), "np": np.float32(2.5)}
+    bench.dump_outputs(str(tmp_path / "a"), named)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in named}
+    assert got["bf"].dtype == np.float32 and np.array_equal(got["bf"], x.numpy())
+    assert got["f64"].dtype == np.float64 and np.array_equal(got["f64"], x.numpy())
+    assert got["i"].dtype == np.float32 and got["i"] == 5 and got["np"] == 2.5
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2 * 40)          # 40 bytes each: 10 floats of `big`
+    big = np.arange(1000, dtype=np.float32)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": np.ones(4, np.float32)})
+    s1, s2 = np.load(tmp_path / "b" / "big.npy"), np.load(tmp_path / "c" / "big.npy")
+    assert s1.shape == (10,) and np.array_equal(s1, s2) and np.all(np.diff(s1) > 0)
+    assert np.load(tmp_path / "b" / "small.npy").shape == (4,)
+    assert sum(f.stat().st_size - 128 for f in (tmp_path / "b").iterdir()) <= 80

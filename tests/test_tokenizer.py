@@ -1,7 +1,10 @@
 """C++ BPE tokenizer (csrc/tokenizer.cpp via clipembed.tokenizer) against golden ids produced by the
 reference's own SimpleTokenizer (tests/golden/make_golden_tokenizer.py; ftfy stubbed to identity in
-both).  Needs the BPE merges file (OpenAI data, not redistributed): $CLIPEMBED_BPE_PATH, an installed
-open_clip, or the reference tree in the build container; skipped when none is present."""
+both).  CLIP's BPE merges file (OpenAI data) is not part of this repository: where the package finds it
+($CLIPEMBED_BPE_PATH or an installed open_clip) the tests run on it against tests/golden/tokenizer.npz;
+everywhere else they run on the synthetic merges file of the same format and size
+(tests/golden/bpe_synthetic.txt.gz, make_bpe_synthetic.py) against tokenizer_synthetic.npz, which the
+reference's tokenizer produced from that file and the same texts.  They never skip."""
 import os
 
 import numpy as np
@@ -11,17 +14,15 @@ import torch
 from clipembed import tokenizer as T
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-G = np.load(os.path.join(HERE, "golden", "tokenizer.npz"))
-_REF_BPE = "/root/reference/open_clip/src/open_clip/bpe_simple_vocab_16e6.txt.gz"
+try:
+    _BPE, _GOLDEN = T.default_bpe(), "tokenizer.npz"
+except FileNotFoundError:
+    _BPE, _GOLDEN = os.path.join(HERE, "golden", "bpe_synthetic.txt.gz"), "tokenizer_synthetic.npz"
+G = np.load(os.path.join(HERE, "golden", _GOLDEN))
 
 
 def _bpe():
-    try:
-        return T.default_bpe()
-    except FileNotFoundError:
-        if os.path.exists(_REF_BPE):
-            return _REF_BPE
-        pytest.skip("BPE merges file not available")
+    return _BPE
 
 
 @pytest.fixture(scope="module")

@@ -12,6 +12,8 @@
 #   py:<script>,<args>                     any python script (kernel A/B: tools/bench_gemm_epi.py,
 #                                          tools/bench_kernels.py; timelines: tools/gemm_trace.py)
 #   envpy:<VAR=VAL>,<script>,<args>        the same with one environment setting (e.g. CLIPEMBED_LIB=...)
+# bench / envbench run bench.py as given: add --full for the roofline, every_row and cpu_baseline legs;
+# the rocprof / clock / pmc / pmcs steps always pass --full.
 # Every step has its own time limit; the chain stops at the first failure.
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
@@ -21,6 +23,8 @@ for step in "$@"; do
   n=$((n + 1))
   kind=${step%%:*}; arg=${step#*:}; [ "$arg" = "$step" ] && arg=""
   args=${arg//,/ }
+  # the profiling steps trace the whole bench (profile pass, every_row leg included), as their summaries expect
+  case $kind in rocprof|clock|pmc|pmcs) args="$args --full" ;; esac
   case $kind in
     tests)   timeout -k 10 900 python -u -m pytest $args -v --timeout 300 --timeout-method thread \
                > gpurun_out/${TAG}_tests$n.log 2>&1 ;;
