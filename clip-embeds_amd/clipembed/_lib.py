@@ -19,6 +19,7 @@ CE_PRE_CLIP_BICUBIC, CE_PRE_PACL_BILINEAR_AA = 0, 1
 CE_ACT_GELU_ERF, CE_ACT_QUICK_GELU = 0, 1
 CE_PACL_ONES, CE_PACL_SIGMOID10 = 0, 1
 CE_ROPE_NONE, CE_ROPE_BEFORE, CE_ROPE_AFTER = 0, 1, 2
+CE_PREC_BF16, CE_PREC_F32 = 0, 1
 
 
 class TowerConfig(ctypes.Structure):
@@ -118,6 +119,10 @@ _SIGNATURES = {
     "ce_set_ln_fold": (c_int, [c_void_p, c_int, POINTER(c_int)]),
     "ce_set_resid_hl": (c_int, [c_void_p, c_int, POINTER(c_int)]),
     "ce_set_pooled_prune": (c_int, [c_void_p, c_int, POINTER(c_int)]),
+    "ce_set_precision": (c_int, [c_void_p, c_int, POINTER(c_int)]),
+    "ce_kernel_gemm_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_int,
+                                   c_void_p, c_void_p, c_int64]),
+    "ce_kernel_attention_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int]),
     "ce_kernel_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int]),
     "ce_kernel_layernorm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int]),
     "ce_train_bind": (c_int, [c_void_p, POINTER(Tensor), POINTER(Tensor), c_int]),

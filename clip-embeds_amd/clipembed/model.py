@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import ctypes
 import math
+import os
 from typing import Dict, Optional
 
 import numpy as np
@@ -30,6 +31,37 @@ def _stream(device: torch.device):
 
 
 _TORCH_TO_CE = {torch.float32: _lib.CE_F32, torch.bfloat16: _lib.CE_BF16, torch.float16: _lib.CE_F16}
+
+
+PRECISION_ENV = "CLIPEMBED_PRECISION"
+_PRECISIONS = {"bf16": _lib.CE_PREC_BF16, "fp32": _lib.CE_PREC_F32}
+# open_clip's `precision` values (factory.py:241-260) that mean bf16 compute here
+_BF16_NAMES = ("bf16", "amp", "amp_bf16")
+
+
+def _check_precision(name) -> str:
+    if not isinstance(name, str) or name not in _PRECISIONS:
+        raise ValueError(f"precision must be one of {sorted(_PRECISIONS)}, got {name!r}")
+    return name
+
+
+def resolve_precision(precision: Optional[str] = None) -> str:
+    """The engine mode ('bf16' or 'fp32') for an open_clip style `precision` argument: None takes
+    $CLIPEMBED_PRECISION (unset: bf16, the engine default), 'fp32' selects the fp32 mode, 'bf16' /
+    'amp' / 'amp_bf16' select bf16; any other open_clip value raises ValueError."""
+    src = "precision"
+    if precision is None:
+        precision = os.environ.get(PRECISION_ENV) or None
+        src = f"${PRECISION_ENV}"
+        if precision is None:
+            return "bf16"
+    p = str(precision).lower()
+    if p == "fp32":
+        return "fp32"
+    if p in _BF16_NAMES:
+        return "bf16"
+    raise ValueError(f"{src}={precision!r} is not supported: clipembed computes in 'fp32' or in bf16 "
+                     f"({', '.join(repr(n) for n in _BF16_NAMES)})")
 
 
 class Engine:
@@ -120,6 +152,15 @@ class Engine:
         _lib.call("ce_set_pooled_prune", self.h, 1 if on else 0, ctypes.byref(prev))
         return prev.value == 1
 
+    def set_precision(self, name: str) -> str:
+        """'fp32': f32 activations and weights on the f32-input MFMA with exact activations, for
+        decisions identical to an f32 reference; 'bf16' (default): the fast path.  Returns the
+        previous mode.  Weights loaded before a switch to 'fp32' have no f32 copy: load them again
+        (CLIP.set_precision does), or the encoders raise (ce_set_precision)."""
+        prev = ctypes.c_int()
+        _lib.call("ce_set_precision", self.h, _PRECISIONS[_check_precision(name)], ctypes.byref(prev))
+        return "fp32" if prev.value == _lib.CE_PREC_F32 else "bf16"
+
     # ---- timing (roofline reporting) ----
     def set_timing(self, on: bool, only: str = ""):
         """Bracket kernel launches with HIP events (all tags, or only the launches tagged `only`)."""
@@ -184,6 +225,7 @@ class CLIP(torch.nn.Module):
         self.logit_bias = None
         self._sd: Dict[str, torch.Tensor] = {}
         self._engine: Optional[Engine] = None
+        self.precision = "bf16"
 
     # ---------------------------------------------------------------- weights / device
     def load_state_dict(self, state_dict, strict: bool = True):
@@ -197,6 +239,17 @@ class CLIP(torch.nn.Module):
         self._sd.update(sd)
         if self._engine is not None:
             self._engine.load(sd, allow_unknown=not strict)
+        return self
+
+    def set_precision(self, name: str):
+        """"fp32" | "bf16" (Engine.set_precision), before or after .to(device); the choice is kept for
+        engines created later.  On a live engine the weights are loaded again, so the fp32 mode's
+        f32 copies exist."""
+        self.precision = _check_precision(name)
+        if self._engine is not None:
+            self._engine.set_precision(name)
+            if self._sd:
+                self._engine.load(self._sd)
         return self
 
     def state_dict(self, *args, **kwargs):
@@ -217,6 +270,8 @@ class CLIP(torch.nn.Module):
             idx = device.index if device.index is not None else torch.cuda.current_device()
             if self._engine is None or self._engine.device.index != idx:
                 self._engine = Engine(self.cfg, idx)
+                if self.precision != "bf16":
+                    self._engine.set_precision(self.precision)
                 if self._sd:
                     self._engine.load(self._sd)
             self.logit_scale.data = self.logit_scale.data.to(device)
@@ -376,15 +431,20 @@ def resolve_pretrained(model_name: str, pretrained: str, quick_gelu: bool = Fals
 
 
 def create_model(model_name: str = "ViT-L-14-336", pretrained: Optional[str] = None, device=None,
-                 state_dict: Optional[dict] = None, output_dict: bool = False, **_ignored) -> CLIP:
+                 state_dict: Optional[dict] = None, output_dict: bool = False, precision: Optional[str] = None,
+                 **_ignored) -> CLIP:
     """open_clip.create_model equivalent (factory.py:241-613) for the registered CLIP configs.
 
     pretrained: None (weights must then be supplied via `state_dict`/load_state_dict), a path to a
     local open_clip state dict (.pt/.bin loaded with weights_only=True, or .safetensors), or a known
     tag ('openai'), resolved to a local file by resolve_pretrained ($CLIPEMBED_PRETRAINED_DIR).
+    precision: None (the engine default, bf16, unless $CLIPEMBED_PRECISION=fp32), 'fp32' (the fp32
+    mode, CLIP.set_precision) or 'bf16' / 'amp' / 'amp_bf16'; other open_clip values raise ValueError.
     """
+    mode = resolve_precision(precision)
     cfg = get_model_config(model_name)
     model = CLIP(cfg, output_dict=output_dict)
+    model.set_precision(mode)
     if pretrained:
         load_checkpoint(model, resolve_pretrained(model_name, pretrained, cfg.quick_gelu))
     if state_dict is not None:
@@ -395,7 +455,7 @@ def create_model(model_name: str = "ViT-L-14-336", pretrained: Optional[str] = N
 
 
 def create_model_and_transforms(model_name: str = "ViT-L-14-336", pretrained: Optional[str] = None,
-                                device=None, **kw):
+                                device=None, precision: Optional[str] = None, **kw):
     """Returns (model, preprocess_train, preprocess_val) like open_clip (factory.py:822-958), both
     transforms on the device (clipembed.transforms.image_transform): preprocess_val = Pillow-exact
     bicubic resize + center crop + normalise; preprocess_train = RandomResizedCrop(scale=(0.9, 1.0))
@@ -403,7 +463,7 @@ def create_model_and_transforms(model_name: str = "ViT-L-14-336", pretrained: Op
     takes the SECOND value (eval_clip.py:21-24), so its What'sUp / MMVP scores use the train one."""
     from .transforms import image_transform
     aug_cfg = kw.pop("aug_cfg", None)
-    model = create_model(model_name, pretrained, device, **kw)
+    model = create_model(model_name, pretrained, device, precision=precision, **kw)
     S = model.cfg.vision.image_size
     return (model, image_transform(S, is_train=True, aug_cfg=aug_cfg, device=device),
             image_transform(S, is_train=False, device=device))

@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from .config import get_model_config
-from .model import CLIP, _ptr, _stream, kernel_engine
+from .model import CLIP, _ptr, _stream, kernel_engine, resolve_precision
 from .weights import synthetic_pacl_heads
 
 
@@ -24,7 +24,8 @@ class open_clip_pacl(torch.nn.Module):
     weight_mode = _lib.CE_PACL_ONES
     rope = _lib.CE_ROPE_NONE
 
-    def __init__(self, base_model: str = "ViT-L-14-336", clip_state_dict=None, device=None, cfg=None):
+    def __init__(self, base_model: str = "ViT-L-14-336", clip_state_dict=None, device=None, cfg=None,
+                 precision=None):
         super().__init__()
         if cfg is None:
             if base_model != "ViT-L-14-336":
@@ -32,6 +33,8 @@ class open_clip_pacl(torch.nn.Module):
             cfg = get_model_config(base_model)
         cfg = cfg.with_pacl(768)
         self.clip_model = CLIP(cfg)
+        # (the reference builds its CLIP with no precision argument, pacl.py:69: None takes the environment)
+        self.clip_model.set_precision(resolve_precision(precision))
         self.clip_model.visual.output_tokens = True          # pacl.py:100
         if clip_state_dict is not None:
             self.clip_model.load_state_dict(clip_state_dict)
@@ -61,6 +64,13 @@ class open_clip_pacl(torch.nn.Module):
 
     def to(self, *args, **kwargs):
         self.clip_model.to(*args, **kwargs)
+        if self._heads and self.clip_model._engine is not None:
+            self.clip_model._engine.load(self._heads, allow_unknown=True)
+        return self
+
+    def set_precision(self, name: str):
+        """CLIP.set_precision for the towers and the heads (loaded again on a live engine)."""
+        self.clip_model.set_precision(name)
         if self._heads and self.clip_model._engine is not None:
             self.clip_model._engine.load(self._heads, allow_unknown=True)
         return self

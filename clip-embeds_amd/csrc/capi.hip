@@ -173,6 +173,11 @@ struct ce_handle {
     // rows only (CLS / EOT); env CE_POOLED_PRUNE=0 / ce_set_pooled_prune(h, 0)
     bool pooled_prune = true;
     std::map<std::string, bool> folded;
+    // precision mode (ce_set_precision).  CE_PREC_F32: ce_load_weights also keeps "<name>@f32", an f32
+    // device copy of every bf16-stored matrix (and of in_proj_bias, which the bf16 path stores with
+    // the attention scale folded in); f32ok[name] says that copy is current
+    int precision = CE_PREC_BF16;
+    std::map<std::string, bool> f32ok;
     // text-tower training: caller-owned f32 master values and gradient slots per
     // trainable tensor (device pointers), saved activations of the last ce_text_forward_train
     std::map<std::string, std::pair<float*, float*>> bound;
@@ -834,6 +839,202 @@ int run_text(ce_handle* h, hipStream_t s, const TowerWs& w, const int64_t* ids, 
     return CE_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// fp32 precision mode (CE_PREC_F32, exact.hip): the straight unfolded sequence of run_block with
+// f32 activations and f32 weights; no LN fold, no hi/lo planes, no pooled prune, no packed rows.
+struct ExactWs {
+    float *x, *xn, *qkv, *att, *hid, *pooled;
+    int* rows;
+    float *lin, *h1, *vp;     // PACL visual head [head_rows][Pd] (head_rows == 0: null)
+    size_t end;               // bytes the layout covers
+};
+
+// The one layout of the exact-mode tower buffers: base == null sizes the allocation (.end), else it
+// carves it.  hid also holds the patch columns (extra_hid_elems).
+ExactWs exact_layout(char* base, long rows, int D, int F, long extra_hid_elems, long B, long head_rows, int Pd) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) -> char* {
+        char* r = base ? base + off : nullptr;
+        off += align256(bytes);
+        return r;
+    };
+    ExactWs w;
+    w.x = (float*)take((size_t)rows * D * 4);
+    w.xn = (float*)take((size_t)rows * D * 4);
+    w.qkv = (float*)take((size_t)rows * 3 * D * 4);
+    w.att = (float*)take((size_t)rows * D * 4);
+    w.hid = (float*)take((size_t)std::max(rows * F, extra_hid_elems) * 4);
+    w.pooled = (float*)take((size_t)B * D * 4);
+    w.rows = (int*)take((size_t)B * 4);
+    w.lin = w.h1 = w.vp = nullptr;
+    if (head_rows > 0) {
+        w.lin = (float*)take((size_t)head_rows * Pd * 4);
+        w.h1 = (float*)take((size_t)head_rows * Pd * 4);
+        w.vp = (float*)take((size_t)head_rows * Pd * 4);
+    }
+    w.end = off;
+    return w;
+}
+
+ExactWs exact_vision_layout(const ce_handle* h, char* base, long B, bool head) {
+    const long P = (long)h->G * h->G;
+    return exact_layout(base, B * (P + 1), h->cfg.vision.width, h->cfg.vision.mlp_width, B * P * h->Kp, B,
+                        head ? B * P : 0, h->cfg.pacl_dim);
+}
+ExactWs exact_text_layout(const ce_handle* h, char* base, long B) {
+    return exact_layout(base, B * h->cfg.context_length, h->cfg.text.width, h->cfg.text.mlp_width, 0, B, 0, 0);
+}
+
+// grow `buf` to the layout's size and carve it; the carve's end is checked against the allocation
+template <class Layout>
+int exact_ws(char*& buf, size_t& bytes, Layout&& layout, ExactWs& w) {
+    CE_TRY(grow_buffer(buf, bytes, layout(nullptr).end));
+    w = layout(buf);
+    if (w.end > bytes) return fail(CE_ERR_INVALID, "fp32 workspace: the layout ends at %zu of %zu bytes", w.end, bytes);
+    return CE_OK;
+}
+
+int need_f32(const ce_handle* h, const std::string& name, const float*& out) {
+    auto ok = h->f32ok.find(name);
+    out = W(h, name + "@f32");
+    if (!out || ok == h->f32ok.end() || !ok->second)
+        return fail(CE_ERR_STATE, "fp32 mode: no current f32 copy of '%s' (call ce_load_weights after "
+                                  "ce_set_precision(CE_PREC_F32))", name.c_str());
+    return CE_OK;
+}
+
+struct BlkX {
+    const float *ln1w, *ln1b, *bqkv, *bout, *ln2w, *ln2b, *bfc, *bproj;
+    const float *wqkv, *wout, *wfc, *wproj;
+};
+
+int block_ptrs_exact(const ce_handle* h, const std::string& p, BlkX& b) {
+    b.ln1w = W(h, p + "ln_1.weight");
+    b.ln1b = W(h, p + "ln_1.bias");
+    b.bout = W(h, p + "attn.out_proj.bias");
+    b.ln2w = W(h, p + "ln_2.weight");
+    b.ln2b = W(h, p + "ln_2.bias");
+    b.bfc = W(h, p + "mlp.c_fc.bias");
+    b.bproj = W(h, p + "mlp.c_proj.bias");
+    CE_TRY(need_f32(h, p + "attn.in_proj_bias", b.bqkv));      // (the plain copy carries kAttnQScale)
+    CE_TRY(need_f32(h, p + "attn.in_proj_weight", b.wqkv));
+    CE_TRY(need_f32(h, p + "attn.out_proj.weight", b.wout));
+    CE_TRY(need_f32(h, p + "mlp.c_fc.weight", b.wfc));
+    return need_f32(h, p + "mlp.c_proj.weight", b.wproj);
+}
+
+int gemm_exact(ce_handle* h, hipStream_t s, const char* tag, const float* A, long lda, const float* Wt, int M, int N,
+               int K, const float* bias, int act, const float* resid, float* out, int grp = 0, int o_gs = 0,
+               int o_go = 0, int r_gs = 0, int r_go = 0) {
+    ce::GemmF32Params p{};
+    p.A = A; p.lda = lda; p.W = Wt;
+    p.M = M; p.N = N; p.K = K;
+    p.bias = bias;
+    p.resid = resid; p.ldr = N;
+    p.out = out; p.ldo = N;
+    p.grp = grp; p.o_gs = o_gs; p.o_go = o_go; p.r_gs = r_gs; p.r_go = r_go;
+    const double bytes = 4.0 * ((double)M * K + (double)N * K + (double)M * N * (resid ? 2 : 1));
+    return timed(h, s, tag, 2.0 * M * N * K, bytes, [&] { return ce::launch_gemm_f32(p, act, s); });
+}
+
+// run_block in f32 (transformer.py:257-268) on the stream w.x [B*L][D]
+int run_block_exact(ce_handle* h, hipStream_t s, const ExactWs& w, const BlkX& k, int B, int L, int D, int H, int F,
+                    bool causal, bool vis) {
+    const int M = B * L;
+    CE_TRY(layernorm(h, s, vis ? "ln_v_f32" : "ln_t_f32", w.x, w.xn, false, k.ln1w, k.ln1b, M, D));
+    CE_TRY(gemm_exact(h, s, vis ? "gemm_qkv_v_f32" : "gemm_qkv_t_f32", w.xn, D, k.wqkv, M, 3 * D, D, k.bqkv,
+                      ce::ACT_NONE_, nullptr, w.qkv));
+    CE_TRY(timed(h, s, vis ? "attn_v_f32" : "attn_t_f32", 4.0 * B * H * (double)L * L * 64, (double)M * 4 * D * 4,
+                 [&] { return ce::launch_attention_f32(w.qkv, w.att, B, L, H, causal, s); }));
+    CE_TRY(gemm_exact(h, s, vis ? "gemm_out_v_f32" : "gemm_out_t_f32", w.att, D, k.wout, M, D, D, k.bout, ce::ACT_NONE_,
+                      w.x, w.x));
+    CE_TRY(layernorm(h, s, vis ? "ln_v_f32" : "ln_t_f32", w.x, w.xn, false, k.ln2w, k.ln2b, M, D));
+    CE_TRY(gemm_exact(h, s, vis ? "gemm_fc_v_f32" : "gemm_fc_t_f32", w.xn, D, k.wfc, M, F, D, k.bfc, act_code(h), nullptr,
+                      w.hid));
+    return gemm_exact(h, s, vis ? "gemm_proj_v_f32" : "gemm_proj_t_f32", w.hid, F, k.wproj, M, D, F, k.bproj,
+                      ce::ACT_NONE_, w.x, w.x);
+}
+
+// pooled rows [B][D] (w.pooled, already through the tower's last LayerNorm) -> projection [-> normalise]
+int project_pooled(ce_handle* h, hipStream_t s, const float* pooled, const char* proj, int B, int D, float* out,
+                   bool normalize) {
+    const int E = h->cfg.embed_dim;
+    ce::FGemmParams fp{};
+    fp.A = pooled; fp.lda = D; fp.B = W(h, proj); fp.ldb = E;
+    fp.C = out; fp.ldc = E; fp.M = B; fp.N = E; fp.K = D; fp.batch = 1;
+    fp.alpha = 1.f;
+    CE_TRY(check_launch(ce::launch_fgemm(fp, false, s), proj));
+    if (normalize) CE_TRY(check_launch(ce::launch_l2norm(out, out, B, E, s), "normalize"));
+    return CE_OK;
+}
+
+// run_vision in f32.  Leaves the final residual stream in w.x.  out_pooled may be null.
+int run_vision_exact(ce_handle* h, hipStream_t s, const ExactWs& w, const void* pix, bool pix_bf16, int B,
+                     float* out_pooled, bool normalize) {
+    const ce_config& c = h->cfg;
+    const int D = c.vision.width, G = h->G, P = G * G, Lv = P + 1;
+    const float* wconv = nullptr;
+    CE_TRY(need_f32(h, "visual.conv1.weight", wconv));
+    std::vector<BlkX> blk(c.vision.layers);
+    for (int i = 0; i < c.vision.layers; ++i)
+        CE_TRY(block_ptrs_exact(h, "visual.transformer.resblocks." + std::to_string(i) + ".", blk[i]));
+    CE_TRY(timed(h, s, "im2col_f32", 0.0, (double)B * 3 * c.image_size * c.image_size * (pix_bf16 ? 2 : 4) +
+                                              (double)B * P * h->Kp * 4,
+                 [&] { return ce::launch_im2col_f32(pix, pix_bf16, w.hid, B, c.image_size, c.patch_size, h->Kp, s); }));
+    // conv1 as a patch GEMM: row (b, p) goes to b * Lv + 1 + p with pos[1 + p] added
+    CE_TRY(gemm_exact(h, s, "gemm_patch_f32", w.hid, h->Kp, wconv, B * P, D, h->Kp, nullptr, ce::ACT_NONE_,
+                      W(h, "visual.positional_embedding"), w.x, P, Lv, 1, 0, 1));
+    CE_TRY(check_launch(ce::launch_cls_rows(w.x, W(h, "visual.class_embedding"), W(h, "visual.positional_embedding"),
+                                            B, Lv, D, s), "cls_rows"));
+    CE_TRY(layernorm(h, s, "ln_v_f32", w.x, w.x, false, W(h, "visual.ln_pre.weight"), W(h, "visual.ln_pre.bias"),
+                     B * Lv, D));
+    for (int i = 0; i < c.vision.layers; ++i)
+        CE_TRY(run_block_exact(h, s, w, blk[i], B, Lv, D, c.vision.heads, c.vision.mlp_width, false, true));
+    if (out_pooled) {
+        CE_TRY(check_launch(ce::launch_ln_gather(w.pooled, w.x, nullptr, (long)Lv * D, B, D,
+                                                 W(h, "visual.ln_post.weight"), W(h, "visual.ln_post.bias"), s),
+                            "ln_post(pool)"));
+        CE_TRY(project_pooled(h, s, w.pooled, "visual.proj", B, D, out_pooled, normalize));
+    }
+    return CE_OK;
+}
+
+int run_text_exact(ce_handle* h, hipStream_t s, const ExactWs& w, const int64_t* ids, int B, float* out_pooled,
+                   bool normalize) {
+    const ce_config& c = h->cfg;
+    const int D = c.text.width, L = c.context_length;
+    std::vector<BlkX> blk(c.text.layers);
+    for (int i = 0; i < c.text.layers; ++i)
+        CE_TRY(block_ptrs_exact(h, "transformer.resblocks." + std::to_string(i) + ".", blk[i]));
+    if (out_pooled) CE_TRY(check_launch(ce::launch_argmax_rows(w.rows, ids, B, L, s), "argmax"));
+    CE_TRY(check_launch(ce::launch_text_embed(w.x, ids, W(h, "token_embedding.weight"), W(h, "positional_embedding"),
+                                              B, L, D, c.vocab_size, s), "token_embedding"));
+    for (int i = 0; i < c.text.layers; ++i)
+        CE_TRY(run_block_exact(h, s, w, blk[i], B, L, D, c.text.heads, c.text.mlp_width, true, false));
+    if (out_pooled) {
+        CE_TRY(check_launch(ce::launch_ln_gather(w.pooled, w.x, w.rows, D, B, D, W(h, "ln_final.weight"),
+                                                 W(h, "ln_final.bias"), s), "ln_final(pool)"));
+        CE_TRY(project_pooled(h, s, w.pooled, "text_projection", B, D, out_pooled, normalize));
+    }
+    return CE_OK;
+}
+
+// The PACL visual head (pacl.py:20-50, Patch_Projection) in f32 on LayerNormed rows xn [M][Dv]:
+// out = linear(xn) + non_linear.2(GELU(non_linear.0(xn))); lin and h1 are [M][Pd] scratch
+int pacl_head_exact(ce_handle* h, hipStream_t s, const float* xn, int M, float* lin, float* h1, float* out) {
+    const int Dv = h->cfg.vision.width, Pd = h->cfg.pacl_dim;
+    const float *w0 = nullptr, *w1 = nullptr, *w2 = nullptr;
+    CE_TRY(need_f32(h, "visual_projection.2.linear_projection.0.weight", w0));
+    CE_TRY(need_f32(h, "visual_projection.2.non_linear_projection.0.weight", w1));
+    CE_TRY(need_f32(h, "visual_projection.2.non_linear_projection.2.weight", w2));
+    CE_TRY(gemm_exact(h, s, "gemm_pacl_f32", xn, Dv, w0, M, Pd, Dv, W(h, "visual_projection.2.linear_projection.0.bias"),
+                      ce::ACT_NONE_, nullptr, lin));
+    CE_TRY(gemm_exact(h, s, "gemm_pacl_f32", xn, Dv, w1, M, Pd, Dv,
+                      W(h, "visual_projection.2.non_linear_projection.0.bias"), ce::ACT_GELU_, nullptr, h1));
+    return gemm_exact(h, s, "gemm_pacl_f32", h1, Pd, w2, M, Pd, Pd,
+                      W(h, "visual_projection.2.non_linear_projection.2.bias"), ce::ACT_NONE_, lin, out);
+}
+
 void host_rope_tables(int P, int D, std::vector<float>& cs, std::vector<float>& sn) {
     // mirrors apply_rope's f32 arithmetic: inv_freq = 1/(10000^(2i/D)); angle = pos * inv_freq
     const int half = D / 2;
@@ -1373,6 +1574,23 @@ int ce_load_weights(ce_handle* h, const ce_tensor* t, int n, int allow_unknown) 
         for (auto v : sp.shape) cnt *= (size_t)v;
         CE_TRY(tensor_f32(t[i], cnt, f));
         idx[name] = i;
+        const bool inproj_bias = name.size() > 17 && name.compare(name.size() - 17, 17, "attn.in_proj_bias") == 0;
+        if (sp.st == ST_BF16 || sp.st == ST_BF16_PADK || inproj_bias) {
+            // fp32 mode: the unrounded, unscaled values next to the bf16 copy (conv1 zero padded to Kp)
+            if (h->precision == CE_PREC_F32) {
+                if (sp.st == ST_BF16_PADK) {
+                    const size_t N = (size_t)sp.shape[0], K = cnt / N, Kp = (size_t)h->Kp;
+                    std::vector<float> pad(N * Kp, 0.f);
+                    for (size_t r = 0; r < N; ++r) memcpy(&pad[r * Kp], &f[r * K], K * 4);
+                    CE_TRY(upload_named(h, name + "@f32", pad.data(), pad.size() * 4));
+                } else {
+                    CE_TRY(upload_named(h, name + "@f32", f.data(), cnt * 4));
+                }
+                h->f32ok[name] = true;
+            } else if (h->f32ok.count(name)) {
+                h->f32ok[name] = false;     // a bf16-mode load leaves an older f32 copy stale
+            }
+        }
         // Fold the attention score scale log2(e)/sqrt(head_dim) into the q rows of in_proj (the
         // first third of weight and bias): the attention kernel then works in log2 units with no
         // per-score multiply (attention.hip).  The host-side state dict keeps the original values.
@@ -1446,6 +1664,11 @@ int ce_missing_weights(ce_handle* h, int* n_missing, const char** first_missing)
 int ce_reserve(ce_handle* h, int max_images, int max_texts) {
     if (!h || max_images < 0 || max_texts < 0) return fail(CE_ERR_INVALID, "ce_reserve: bad argument");
     DeviceGuard g(h->device);
+    if (h->precision == CE_PREC_F32) {
+        const size_t tb = exact_text_layout(h, nullptr, max_texts).end;
+        CE_TRY(ensure_ws(h, std::max(exact_vision_layout(h, nullptr, max_images, h->cfg.pacl_dim > 0).end, tb)));
+        return ensure_ws_text(h, tb);
+    }
     CE_TRY(ensure_ws(h, std::max(vision_bytes(h, max_images), text_bytes(h, max_texts))));
     return ensure_ws_text(h, text_bytes(h, max_texts));
 }
@@ -1462,9 +1685,18 @@ int ce_encode_image(ce_handle* h, void* stream, const void* pixels, int pixel_dt
     CE_TRY(check_ready(h, false));
     DeviceGuard g(h->device);
     hipStream_t s = (hipStream_t)stream;
-    CE_TRY(ensure_ws(h, vision_bytes(h, B)));
     const long P = (long)h->G * h->G, Lv = P + 1;
     const int D = h->cfg.vision.width;
+    if (h->precision == CE_PREC_F32) {
+        ExactWs w;
+        CE_TRY(exact_ws(h->ws, h->ws_bytes, [&](char* b) { return exact_vision_layout(h, b, B, false); }, w));
+        CE_TRY(run_vision_exact(h, s, w, pixels, pixel_dtype == CE_BF16, B, out_pooled, normalize != 0));
+        if (out_tokens)
+            CE_TRY(layernorm(h, s, "ln_v_f32", w.x, out_tokens, tokens_dtype == CE_BF16, W(h, "visual.ln_post.weight"),
+                             W(h, "visual.ln_post.bias"), (int)(B * P), D, (int)P, (int)Lv, 1, (int)P, 0));
+        return CE_OK;
+    }
+    CE_TRY(ensure_ws(h, vision_bytes(h, B)));
     TowerWs w = carve(h->ws, B * Lv, D, h->cfg.vision.mlp_width, B * P * h->Kp, B);
     CE_TRY(run_vision(h, s, w, pixels, pixel_dtype == CE_BF16, B, out_pooled, normalize != 0, out_tokens != nullptr));
     if (out_tokens)
@@ -1485,8 +1717,17 @@ int ce_encode_text(ce_handle* h, void* stream, const int64_t* ids, int B, int ct
     CE_TRY(check_ready(h, false));
     DeviceGuard g(h->device);
     hipStream_t s = (hipStream_t)stream;
-    CE_TRY(ensure_ws_text(h, text_bytes(h, B)));
     const int D = h->cfg.text.width;
+    if (h->precision == CE_PREC_F32) {
+        ExactWs w;
+        CE_TRY(exact_ws(h->ws_t, h->ws_t_bytes, [&](char* b) { return exact_text_layout(h, b, B); }, w));
+        CE_TRY(run_text_exact(h, s, w, ids, B, out_pooled, normalize != 0));
+        if (out_tokens)
+            CE_TRY(layernorm(h, s, "ln_final_t_f32", w.x, out_tokens, tokens_dtype == CE_BF16, W(h, "ln_final.weight"),
+                             W(h, "ln_final.bias"), B * ctx, D));
+        return CE_OK;
+    }
+    CE_TRY(ensure_ws_text(h, text_bytes(h, B)));
     TowerWs w = carve(h->ws_t, (long)B * ctx, D, h->cfg.text.mlp_width, 0, B);
     CE_TRY(run_text(h, s, w, ids, B, out_pooled, normalize != 0, out_tokens != nullptr));
     if (out_tokens)
@@ -1549,6 +1790,36 @@ int ce_pacl_project_patches(ce_handle* h, void* stream, const void* tokens, int 
     hipStream_t s = (hipStream_t)stream;
     const int Dv = h->cfg.vision.width, Pd = h->cfg.pacl_dim;
     const long M = (long)B * P;
+    if (h->precision == CE_PREC_F32) {
+        // scratch: rope f32 M*Dv | xn f32 M*Dv | lin, h1, out f32 M*Pd each; one layout sizes and carves it
+        struct { float *rot, *xn, *lin, *h1, *o; size_t end; } x;
+        auto layout = [&](char* base) {
+            size_t off = 0;
+            auto take = [&](size_t bytes) { char* r = base ? base + off : nullptr; off += align256(bytes); return (float*)r; };
+            x.rot = take(rope ? M * Dv * 4 : 0);
+            x.xn = take(M * Dv * 4);
+            x.lin = take(M * Pd * 4);
+            x.h1 = take(M * Pd * 4);
+            x.o = take(out_dtype == CE_BF16 ? M * Pd * 4 : 0);
+            x.end = off;
+        };
+        layout(nullptr);
+        CE_TRY(ensure_ws(h, x.end));
+        layout(h->ws);
+        if (x.end > h->ws_bytes) return fail(CE_ERR_INVALID, "ce_pacl_project_patches: fp32 workspace overrun");
+        const float* src = (const float*)tokens;
+        if (rope) {
+            CE_TRY(check_launch(ce::launch_rope(x.rot, src, B, P, Dv, h->rc_v, h->rs_v, s), "apply_rope"));
+            src = x.rot;
+        }
+        CE_TRY(layernorm(h, s, "ln_pacl_f32", src, x.xn, false, W(h, "visual_projection.0.weight"),
+                         W(h, "visual_projection.0.bias"), (int)M, Dv));
+        float* o = out_dtype == CE_BF16 ? x.o : (float*)out_proj;
+        CE_TRY(pacl_head_exact(h, s, x.xn, (int)M, x.lin, x.h1, o));
+        if (out_dtype == CE_BF16)
+            CE_TRY(check_launch(ce::launch_f32_to_bf16((bf16_t*)out_proj, o, M * Pd, s), "f32_to_bf16"));
+        return CE_OK;
+    }
     // scratch: [rope f32 M*Dv] | xn bf16 M*Dv | lin f32 M*Pd | h1 bf16 M*Pd
     const size_t need = align256(rope ? M * Dv * 4 : 0) + align256(M * Dv * 2) + align256(M * Pd * 4) + align256(M * Pd * 2);
     CE_TRY(ensure_ws(h, need));
@@ -1642,14 +1913,24 @@ int ce_pacl_forward(ce_handle* h, void* stream, const void* pixels, int pixel_dt
     const int E = c.embed_dim, Pd = c.pacl_dim, Dv = c.vision.width;
     const long P = (long)h->G * h->G, Lv = P + 1;
     // aux (must survive both towers): tclip [Bt,E] | tp [Bt,Pd]
-    CE_TRY(ensure_ws(h, std::max(vision_bytes(h, Bi), text_bytes(h, Bt))));
+    const bool exact = h->precision == CE_PREC_F32;
+    const size_t ws_need = exact ? std::max(exact_vision_layout(h, nullptr, Bi, true).end,
+                                            exact_text_layout(h, nullptr, Bt).end)
+                                 : std::max(vision_bytes(h, Bi), text_bytes(h, Bt));
+    CE_TRY(ensure_ws(h, ws_need));
     CE_TRY(ensure_tmp(h, align256((size_t)Bt * E * 4) + align256((size_t)Bt * Pd * 4) + align256((size_t)Bt * E * 4)));
     float* tclip = (float*)h->tmp;
     float* tp = (float*)(h->tmp + align256((size_t)Bt * E * 4));
     // 1) text tower + PACL text head (pacl.py:116-118)
     {
-        TowerWs w = carve(h->ws, (long)Bt * c.context_length, c.text.width, c.text.mlp_width, 0, Bt);
-        CE_TRY(run_text(h, s, w, ids, Bt, tclip, false, false));
+        if (exact) {
+            ExactWs w;
+            CE_TRY(exact_ws(h->ws, h->ws_bytes, [&](char* b) { return exact_text_layout(h, b, Bt); }, w));
+            CE_TRY(run_text_exact(h, s, w, ids, Bt, tclip, false));
+        } else {
+            TowerWs w = carve(h->ws, (long)Bt * c.context_length, c.text.width, c.text.mlp_width, 0, Bt);
+            CE_TRY(run_text(h, s, w, ids, Bt, tclip, false, false));
+        }
         float* ln = (float*)h->tmp + 0;
         ln = (float*)(h->tmp + align256((size_t)Bt * E * 4) + align256((size_t)Bt * Pd * 4));
         CE_TRY(check_launch(ce::launch_ln_gather(ln, tclip, nullptr, E, Bt, E, W(h, "text_projection.0.weight"),
@@ -1660,6 +1941,19 @@ int ce_pacl_forward(ce_handle* h, void* stream, const void* pixels, int pixel_dt
         CE_TRY(check_launch(ce::launch_fgemm(fp, false, s), "pacl text linear"));
     }
     // 2) vision tower, tokens -> ln_post -> [rope] -> PACL LN (one fused row kernel) -> heads
+    if (exact) {
+        ExactWs w;
+        CE_TRY(exact_ws(h->ws, h->ws_bytes, [&](char* b) { return exact_vision_layout(h, b, Bi, true); }, w));
+        CE_TRY(run_vision_exact(h, s, w, pixels, pixel_dtype == CE_BF16, Bi, nullptr, false));
+        const int M = (int)(Bi * P);
+        CE_TRY(layernorm(h, s, "ln_pacl_f32", w.x, w.xn, false, W(h, "visual.ln_post.weight"),
+                         W(h, "visual.ln_post.bias"), M, Dv, (int)P, (int)Lv, 1, (int)P, 0,
+                         W(h, "visual_projection.0.weight"), W(h, "visual_projection.0.bias"),
+                         rope == CE_ROPE_BEFORE ? h->rc_v : nullptr, rope == CE_ROPE_BEFORE ? h->rs_v : nullptr, (int)P));
+        CE_TRY(pacl_head_exact(h, s, w.xn, M, w.lin, w.h1, w.vp));
+        return ce_pacl_pool(h, stream, w.vp, CE_F32, Bi, (int)P, tp, Bt, Pd, weight_mode, rope == CE_ROPE_AFTER,
+                            out_img, out_txt);
+    }
     TowerWs w = carve(h->ws, Bi * Lv, Dv, c.vision.mlp_width, Bi * P * h->Kp, Bi);
     CE_TRY(run_vision(h, s, w, pixels, pixel_dtype == CE_BF16, Bi, nullptr, false));
     const int M = (int)(Bi * P);
@@ -2620,6 +2914,51 @@ int ce_set_pooled_prune(ce_handle* h, int enable, int* previous) {
     return CE_OK;
 }
 
+int ce_set_precision(ce_handle* h, int precision, int* previous) {
+    if (!h) return fail(CE_ERR_INVALID, "ce_set_precision: null handle");
+    if (precision != CE_PREC_BF16 && precision != CE_PREC_F32)
+        return fail(CE_ERR_INVALID, "ce_set_precision: unknown precision %d", precision);
+    if (previous) *previous = h->precision;
+    h->precision = precision;
+    if (precision == CE_PREC_BF16) {
+        // the f32 copies go: the default mode's footprint is the bf16 weights alone
+        DeviceGuard g(h->device);
+        bool synced = false;
+        for (auto it = h->dptr.begin(); it != h->dptr.end();) {
+            const std::string& n = it->first;
+            if (n.size() > 4 && n.compare(n.size() - 4, 4, "@f32") == 0) {
+                if (!synced) HIP_TRY(hipDeviceSynchronize());
+                synced = true;
+                (void)hipFree(it->second);
+                it = h->dptr.erase(it);
+            } else {
+                ++it;
+            }
+        }
+        h->f32ok.clear();
+    }
+    return CE_OK;
+}
+
+int ce_kernel_gemm_f32(void* stream, const float* A, int64_t lda, const float* Wt, int M, int N, int K,
+                       const float* bias, int act, const float* resid, float* out, int64_t ldo) {
+    if (!A || !Wt || !out) return fail(CE_ERR_INVALID, "ce_kernel_gemm_f32: null argument");
+    if (M <= 0 || N <= 0 || K <= 0 || K % 32 || N % 64 || lda < K || lda % 4 || ldo < N)
+        return fail(CE_ERR_INVALID, "ce_kernel_gemm_f32: need M,N,K > 0, K %% 32 == 0, N %% 64 == 0, lda >= K (%% 4), "
+                    "ldo >= N (got %d %d %d, lda %lld, ldo %lld)", M, N, K, (long long)lda, (long long)ldo);
+    if (act < 0 || act > 2) return fail(CE_ERR_INVALID, "ce_kernel_gemm_f32: bad act %d", act);
+    ce::GemmF32Params p{};
+    p.A = A; p.lda = lda; p.W = Wt; p.M = M; p.N = N; p.K = K; p.bias = bias;
+    p.resid = resid; p.ldr = ldo; p.out = out; p.ldo = ldo;
+    return check_launch(ce::launch_gemm_f32(p, act, (hipStream_t)stream), "gemm_f32");
+}
+
+int ce_kernel_attention_f32(void* stream, const float* qkv, float* out, int B, int L, int H, int causal) {
+    if (!qkv || !out) return fail(CE_ERR_INVALID, "ce_kernel_attention_f32: null argument");
+    if (B <= 0 || L <= 0 || H <= 0) return fail(CE_ERR_INVALID, "ce_kernel_attention_f32: bad sizes");
+    return check_launch(ce::launch_attention_f32(qkv, out, B, L, H, causal != 0, (hipStream_t)stream), "attention_f32");
+}
+
 int ce_kernel_attention(void* stream, const void* qkv, void* out, int B, int L, int H, int causal) {
     if (!qkv || !out) return fail(CE_ERR_INVALID, "ce_kernel_attention: null argument");
     if (B <= 0 || L <= 0 || H <= 0) return fail(CE_ERR_INVALID, "ce_kernel_attention: bad sizes");
@@ -2691,6 +3030,11 @@ int ce_train_sync_weights(ce_handle* h, void* stream) {
     // runs the unfolded text blocks until the tower is loaded again
     for (auto& kv : h->folded)
         if (kv.first.rfind("transformer.resblocks.", 0) == 0) kv.second = false;
+    // and so are their fp32-mode copies
+    for (auto& kv : h->bound) {
+        auto it = h->f32ok.find(kv.first);
+        if (it != h->f32ok.end()) it->second = false;
+    }
     return CE_OK;
 }
 

@@ -142,6 +142,30 @@ hipError_t launch_attention_rows(const bf16_t* qkv, const int* qrows, bf16_t* ou
                                  const bf16_t* wq = nullptr, const float* cq = nullptr, const float* dq = nullptr,
                                  const float2* stats = nullptr);
 
+// ---- fp32 precision mode (exact.hip): f32 operands on the f32-input MFMA, one accumulator chain per
+// output element over all of K ----
+// out[map_o(m)][n] = act(sum_k A[m][k] * W[n][k] + bias[n]) + resid[map_r(m)][n]
+//   A [M][K] f32 (row stride lda, % 4), W [N][K] f32 (nn.Linear layout), bias f32 [N] (nullable), resid f32
+//   (nullable, row stride ldr, may alias out), out f32 (row stride ldo); map_x as GemmParams.
+//   Any M >= 1 (rows clipped), N % 64 == 0, K % 32 == 0, A and W 16-B aligned.
+//   act: exact GELU 0.5 x (1 + erff(x / sqrt 2)) / QuickGELU x / (1 + expf(-1.702 x)) of the device library.
+struct GemmF32Params {
+    const float* A; long lda;
+    const float* W;
+    int M, N, K;
+    const float* bias;
+    const float* resid; long ldr;
+    float* out; long ldo;
+    int grp, o_gs, o_go, r_gs, r_go;
+};
+hipError_t launch_gemm_f32(const GemmF32Params& p, int act, hipStream_t s);
+// qkv [B*L][3*H*64] f32 (q | k | v as launch_attention, nothing pre-scaled) -> out [B*L][H*64] f32:
+// softmax(q k^T / 8 [+ causal]) v with the running row maximum, expf; any L >= 1
+hipError_t launch_attention_f32(const float* qkv, float* out, int B, int L, int H, bool causal, hipStream_t s);
+// launch_im2col with f32 columns
+hipError_t launch_im2col_f32(const void* pix, bool pix_bf16, float* cols, int B, int S, int patch, int Kp,
+                             hipStream_t s);
+
 // LayerNorm over rows of width D (eps 1e-5, affine), f32 in, f32 or bf16 out.
 //   in row  = (r / grp) * i_gs + i_go + r % grp   (grp == 0: identity)
 //   out row = (r / grp) * o_gs + o_go + r % grp

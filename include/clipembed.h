@@ -436,6 +436,29 @@ int ce_set_resid_hl(ce_handle* h, int enable, int* previous);
  * Default on with the LN-folded hi/lo towers (env CE_POOLED_PRUNE=0 at ce_create turns it off);
  * *previous (may be null) gets the previous setting. */
 int ce_set_pooled_prune(ce_handle* h, int enable, int* previous);
+/* Precision mode of a handle (default CE_PREC_BF16; per handle, like ce_set_ln_fold).  CE_PREC_F32
+ * runs both towers and the PACL visual head with f32 activations and f32 weights on the f32-input
+ * MFMA (one k-ordered fmaf chain per output element), f32 attention with the true running row
+ * maximum, and the exact activations (nn.GELU by erff, transformer.py:235-239; QuickGELU by expf,
+ * transformer.py:32-35), so that the strict `>` decisions of the eval drivers (eval_clip.py:58-65,
+ * 318-331; eval_sparc.py:26-56; eval_pacl.py:49-57) match an f32 reference.  No LN fold, hi/lo
+ * planes, pooled prune or packed text rows in this mode.  While it is set, ce_load_weights also
+ * keeps an f32 device copy of every bf16-stored matrix (about +1.55 GB for ViT-L/14-336): set the
+ * mode first, then load.  An encode call whose f32 copy is missing or stale returns CE_ERR_STATE
+ * and names the tensor; there is no fall-back to bf16.  Setting CE_PREC_BF16 frees the copies.
+ * ce_encode_image / ce_encode_text / ce_pacl_project_patches / ce_pacl_forward / ce_reserve follow
+ * the mode; the training entry points ignore it.  *previous (may be null) gets the previous mode. */
+enum ce_precision { CE_PREC_BF16 = 0, CE_PREC_F32 = 1 };
+int ce_set_precision(ce_handle* h, int precision, int* previous);
+/* The fp32 mode's GEMM: out = act(A W^T + bias) + resid (nn.Linear, transformer.py:235-239).
+ * A [M,K] f32 (row stride lda, % 4), Wt [N,K] f32, bias [N] / resid [M,N] f32 nullable (resid shares
+ * out's row stride ldo and may alias out), out f32.  M >= 1, N % 64 == 0, K % 32 == 0, A and Wt
+ * 16-byte aligned.  act: 0 none, 1 exact-erf GELU, 2 QuickGELU. */
+int ce_kernel_gemm_f32(void* stream, const float* A, int64_t lda, const float* Wt, int M, int N, int K,
+                       const float* bias, int act, const float* resid, float* out, int64_t ldo);
+/* The fp32 mode's attention core: packed qkv [B*L, 3*H*64] f32 (nothing pre-scaled) -> out
+ * [B*L, H*64] f32, softmax(q k^T / 8 [+ causal]) v (transformer.py:242-255); any L >= 1. */
+int ce_kernel_attention_f32(void* stream, const float* qkv, float* out, int B, int L, int H, int causal);
 /* Attention core over packed qkv [B*L, 3*H*64] bf16 -> out [B*L, H*64] bf16 (transformer.py:242-255). */
 int ce_kernel_attention(void* stream, const void* qkv, void* out, int B, int L, int H, int causal);
 /* LayerNorm rows [rows, D] f32 -> f32/bf16 (eps 1e-5; transformer.py:23-29).  D % 256 == 0. */
